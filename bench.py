@@ -13,8 +13,13 @@ max-over-ranks timing).  Default --scaling strong: ONE genome's (sequence, k) sp
 split into N equal owned ranges (the metric's "contig-sharded 1->8"); --scaling weak
 gives every rank a config-sized contig set of its own.
 
-Prints ONE JSON line on rank 0; exits 1 if the GPU hit list differs from the CPU
-oracle's on the baseline sample.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps,
+writes the last timed step's hit list if --dump-outputs DIR is given, and prints ONE JSON line
+on rank 0: the headline figure and what describes the run.  --full adds everything else, each
+with runs of its own after the timed steps: the single-search latency, the scan kernel's and
+the stages' times, the roofline (live rocprofv3 counter and trace passes), the host-bytes-to-text
+pass, the CPU baselines and the parity checks; it exits 1 if the GPU hit list differs from the
+CPU oracle's on the baseline sample (or, N > 1 and shards, from the single-device list).
 """
 
 from __future__ import annotations
@@ -111,8 +116,9 @@ def pmc_counters(csv_path: str) -> dict:
 
 def pmc_child_args(argv):
     """The caller's workload options for a counter pass, without its step counts and extras."""
-    skip = {"--gpus", "--steps", "--warmup", "--cpu-budget", "--cpu-threads", "--handles", "--streams", "--depth"}
-    flags = {"--no-cpu-baseline", "--no-e2e", "--no-ref-model", "--e2e-file", "--no-pmc", "--pmc-child"}
+    skip = {"--gpus", "--steps", "--warmup", "--cpu-budget", "--cpu-threads", "--handles", "--streams", "--depth",
+            "--dump-outputs"}
+    flags = {"--no-cpu-baseline", "--no-e2e", "--no-ref-model", "--e2e-file", "--no-pmc", "--pmc-child", "--full"}
     child, i = [], 0
     while i < len(argv):
         a = argv[i]
@@ -465,6 +471,35 @@ def end_to_end_file(sts_path, names, lens, buf, offs, cfg, device):
                     "time (interpreter start, FASTA parse, upload + pack, search, format, write); not the metric"}
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240  # the fixed sample of a hit list too long for it
+
+
+def dump_outputs(out_dir: str, hits, max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """Write a step's hit list (what mp_search_fetch hands its caller, in the list's device order)
+    as out_dir/hits_<field>.npy, one float64 array per field of the hit (pos1, pos2, seq, rec: all
+    below 2^53, so exact), and its length as out_dir/n_hits.npy.  A list too long for max_bytes
+    is cut to a fixed, seeded sample of its rows (the same rows for the same length), kept in
+    list order, and their indices are written too (hits_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(hits)
+    fields = list(hits.dtype.names)
+    rows = (max_bytes - 8) // (8 * (len(fields) + 1))
+    idx = None
+    if n > rows:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=rows, replace=False))
+        hits = hits[idx]
+    written = {"n_hits": 1}
+    np.save(os.path.join(out_dir, "n_hits.npy"), np.array([n], dtype=np.float64))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "hits_index.npy"), idx.astype(np.float64))
+        written["hits_index"] = len(idx)
+    for f in fields:
+        np.save(os.path.join(out_dir, f"hits_{f}.npy"), np.ascontiguousarray(hits[f], dtype=np.float64))
+        written[f"hits_{f}"] = len(hits)
+    return written
+
+
 def free_port() -> int:
     """A TCP port on 127.0.0.1 that nothing listens on right now (the child job's rendezvous)."""
     import socket
@@ -504,8 +539,15 @@ def main():
                          "the N-rank job itself (default: WORLD_SIZE, else 1)")
     # 20 timed steps: the pipeline fills at the first and drains at the last, which 5 steps
     # carried as ~2% of c3's step (2.068 against 2.015-2.03 ms with 10-20 steps)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline figure: "
+                         "single-search latency, scan and stage times, roofline (live rocprofv3 passes), "
+                         "host-bytes-to-text pass, CPU baselines and parity (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's hit list (rank 0's gathered list for N > 1) as "
+                         "DIR/hits_<field>.npy (float64) and DIR/n_hits.npy")
     ap.add_argument("--config", default="c3", choices=["c2", "c3", "c4", "c5"])
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the config's genome and STS set")
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-baseline work")
@@ -546,6 +588,8 @@ def main():
     ap.add_argument("--opts", default="",
                     help="diagnostic A/B: search options for every handle, name=value[,...] (_native.Search.set_options)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # N > 1 and no launcher: start the N-rank job as a child before anything touches the GPU
     # (this process never initialises HIP), and exit with its code
     world, launch = resolve_world(args.gpus, os.environ)
@@ -790,10 +834,15 @@ def main():
             h.close()
         print(json.dumps({"pmc_child": True, "runs": args.warmup + args.steps}), flush=True)
         return
-    # single-search latency beside the pipelined step: handle 0 alone, each run enqueued only
-    # after the previous one completed (host turnaround included, no events), median of 5
+    # the last timed step's hit list, as the handle that ran it hands it to its caller
+    last_j = (args.steps - 1) % nbuf
+    dump_hits = None
+    if args.dump_outputs and world == 1:
+        dump_hits = handles[last_j].fetch(handles[last_j].last_hits(), streams[last_j].cuda_stream)
+    # --full: single-search latency beside the pipelined step: handle 0 alone, each run enqueued
+    # only after the previous one completed (host turnaround included, no events), median of 5
     single_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         torch.cuda.synchronize()
         search.set_scan_timing(False)
         search.set_stage_timing(False)
@@ -804,25 +853,26 @@ def main():
             search.complete()
             lat.append(time.perf_counter() - t1)
         single_ms = float(np.median(lat)) * 1e3
-    # untimed: three more steps of handle 0 alone (the scan time when the timed steps carried
-    # no events), the last with every stage timed (the stage breakdown)
+    # --full, untimed: three more steps of handle 0 alone (the scan time when the timed steps
+    # carried no events), the last with every stage timed (the stage breakdown)
     torch.cuda.synchronize()
     for j in range(nbuf):
         gdone[j] = None
-    search.set_scan_timing(True)
-    scan_ms.clear()
-    for u in range(3):
-        search.set_stage_timing(u == 2)
-        search.enqueue(rng, stream)
-        finish(0)
-        torch.cuda.synchronize()
-        gdone[0] = None
-    if not timed_scan_ms:
-        timed_scan_ms = list(scan_ms)
-    scan_ms = timed_scan_ms
-    stages = search.last_stats()
-    tail_ms, pair_ms, order_ms = [stages["tail_ms"]], [stages["pair_ms"]], [stages["order_ms"]]
-    st = search.last_stats()
+    if args.full:
+        search.set_scan_timing(True)
+        scan_ms.clear()
+        for u in range(3):
+            search.set_stage_timing(u == 2)
+            search.enqueue(rng, stream)
+            finish(0)
+            torch.cuda.synchronize()
+            gdone[0] = None
+        if not timed_scan_ms:
+            timed_scan_ms = list(scan_ms)
+        scan_ms = timed_scan_ms
+        stages = search.last_stats()
+        tail_ms, pair_ms, order_ms = [stages["tail_ms"]], [stages["pair_ms"]], [stages["order_ms"]]
+        st = search.last_stats()
     for h in handles[1:]:
         h.close()
     if world > 1:
@@ -835,19 +885,23 @@ def main():
     else:
         tot_bases = float(sum(lens))
     tot_hits = float(nhits)  # after the gather: every rank's hits (N > 1)
-    dist_check = None
-    if world > 1 or args.shard_of > 1:
-        got = None
-        if ipcg is not None:  # collective: the untimed steps' puts (slot 0) may need a regrow too
+    dist_check, got = None, None
+    if world > 1 and (args.full or args.dump_outputs):  # rank 0: the gathered list of the last step run
+        if ipcg is not None:
             torch.cuda.synchronize()
             torch.distributed.barrier()
-            ipcg.settle()
-        if world > 1 and rank == 0:
+            if args.full:  # collective: the untimed steps' puts (slot 0) may need a regrow too
+                ipcg.settle()
+        if rank == 0:
             if ipcg is not None:
-                raw = ipcg.hits([len(lens) * r for r in range(world)] if weak else None).cpu().numpy()
+                raw = ipcg.hits([len(lens) * r for r in range(world)] if weak else None,
+                                slot=0 if args.full else last_j).cpu().numpy()
             else:
                 raw = (gathered[:nhits * HIT_BYTES] if comm is not None else last_gloo[0]).cpu().numpy()
             got = np.frombuffer(raw.tobytes(), dtype=_native.HIT_DTYPE)
+            if args.dump_outputs:
+                dump_hits = got
+    if args.full and (world > 1 or args.shard_of > 1):
         dist_check = parity_distributed(table, genome, search, rng, got, world, rank, weak, len(lens), stream)
     if ipcg is not None:  # every rank unmaps before rank 0's buffers go
         ipcg.close()
@@ -859,19 +913,8 @@ def main():
         return
     bases = float(sum(lens))          # one rank's genome (= the whole job's at N=1 or strong)
     t_step = elapsed / args.steps
-    kern_ev_s = float(np.mean(scan_ms)) / 1e3  # HIP events on the scan's launch stream
-    alg_bytes = BYTES_PER_BASE * st["windows"] + BYTES_PER_HIT * search.last_hits()  # rank 0's scan launch
-    # the scan stage's kernels (events around all of them): a split W 7..9 table scans its two
-    # exact seeds with scan_kernel (plus dense_kernel over the records they cannot carry)
-    sp = table.split()
-    if sp["seed_tables"]:
-        W = cfg["W"]
-        scan_label = (f"mp::scan_kernel x{sp['seed_tables']} (split seeds: exact [0, 11)"
-                      + (f" + gapped [0, {W}) ++ [11, {22 - W})" if sp["seed_tables"] > 1 else "")
-                      + (f" + dense_kernel over {sp['rest_records']} records" if sp["rest_records"] else "")
-                      + "; one stage, HIP events around all of it)")
-    else:
-        scan_label = "mp::dense_kernel" if cfg["W"] <= 9 else "mp::scan_kernel"
+    if dump_hits is not None:
+        log(f"--dump-outputs: wrote {dump_outputs(args.dump_outputs, dump_hits)} to {args.dump_outputs}")
     workload = (f"{args.config}: {n_sts} STS vs {bases / 1e9:.3f} Gbp ({len(lens)} records), "
                 f"W={cfg['W']} N={cfg['N']} M={cfg['M']} I={cfg['I']}")
     if world > 1 and weak:
@@ -881,23 +924,6 @@ def main():
         gmode, f"N > 1 hit gather: --gather {args.gather}")
     from merpcr_amd._build import source_digest
     build = source_digest()
-    # roofline.traffic / issue: counters measured now, in child passes of this very command;
-    # failing that, a committed profile of this same build; else null with the reason
-    pmc, pmc_src, traffic, why = None, None, None, "not measured for N > 1 or shard runs"
-    if world == 1 and args.shard_of <= 1:
-        regex = "scan_kernel|dense_kernel" if (sp["seed_tables"] or cfg["W"] <= 9) else "scan_kernel"
-        live, why = (None, "--no-pmc") if args.no_pmc else live_pmc(sys.argv[1:], regex)
-        if live is not None:
-            pmc, pmc_src = live, why
-            traffic = 2.0 * live["FETCH_SIZE"] * 1024 + live["WRITE_SIZE"] * 1024
-        else:
-            log(f"live counters unavailable ({why}); looking for a committed profile of build {build}")
-            prof, tag = pmc_profile(workload, build)
-            if prof is not None:
-                pmc, pmc_src = prof, f"profiles/{tag}_pmc.json (committed profile of this build)"
-                traffic = prof["hbm_traffic_bytes_per_launch"]
-    kern_s, kern_src = roofline_time(pmc, kern_ev_s)
-    achieved = alg_bytes / kern_s / 1e9 if kern_s > 0 else 0.0
     out = {
         "metric": METRIC,
         "value": round(tot_bases / max(args.shard_of, 1) / t_step / 1e9, 4),
@@ -906,7 +932,6 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(t_step * 1e3, 3),
-        "single_run_ms": round(single_ms, 3) if single_ms is not None else None,
         "higher_is_better": True,
         "scaling": "weak" if weak else "strong",
         "vs_baseline": None,
@@ -919,39 +944,15 @@ def main():
                                    else f"owned (sequence, k) ranges x{world} of one genome ({gather_label})")},
         "hits": int(tot_hits),
         "hits_per_s": round(tot_hits / t_step, 1),
-        "scan_kernel_ms": round(kern_s * 1e3, 3),
-        "scan_kernel_ms_source": kern_src,
-        "scan_kernel_ms_events": round(kern_ev_s * 1e3, 3),
-        "tail_kernel_ms": round(float(np.mean(tail_ms)), 3),
-        "pair_kernel_ms": round(float(np.mean(pair_ms)), 3),
-        "order_ms": round(float(np.mean(order_ms)), 3),
-        "survivors": st["survivors"],
-        "kernel_gbps_bases": round(st["windows"] / kern_s / 1e9, 3) if kern_s > 0 else None,
-        "candidates": st["candidates"],
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 5),
-                     "traffic": int(traffic) if traffic else None,
-                     "traffic_source": (pmc_src + "; 2 x FETCH_SIZE KiB (gfx950 half-count) + WRITE_SIZE KiB, "
-                                        "Infinity-Cache hits included") if traffic else None,
-                     "traffic_null_reason": None if traffic else why,
-                     "kernel": scan_label,
-                     "alg_bytes_per_launch": int(alg_bytes),
-                     "time_ms": round(kern_s * 1e3, 4),
-                     "time_source": kern_src,
-                     "trace_forms": (pmc or {}).get("_trace_forms"),
-                     "issue": (dict(issue_bound(pmc, kern_s * 1e9), source=pmc_src) if pmc else None)},
         "build": build,
         "setup_s": round(setup_s, 2),
-        "single_run_note": "one isolated search (enqueue -> complete, host turnaround included) on one handle, "
-                           "median of 5 after the timed steps; ms_per_step is the pipelined throughput",
         "pipeline": (f"{nbuf} search handles on {'one stream' if args.one_stream else f'{nstr} streams'}: step i+{depth} "
                      f"enqueued before the host waits for step i (mp_search_enqueue/complete)"
                      if nbuf > 1 else "none: each step waits for the previous"),
-        "scan_timing": ("HIP events around the scan kernel on its launch stream in every timed step"
-                        if scan_in_timed else
-                        "HIP events around the scan kernel on its launch stream in 3 untimed steps after the "
-                        "timed ones, run one at a time (in the timed steps kernels of consecutive steps overlap)"),
+        "full": args.full,
     }
+    if args.dump_outputs:
+        out["dump_outputs"] = args.dump_outputs
     if args.opts:
         out["search_options"] = args.opts
     if args.shard_of > 1:
@@ -959,21 +960,82 @@ def main():
     if args.rehearse_one_gpu:
         out["diagnostic"] = f"{world} ranks sharing device 0 (rehearsal of the N-rank path, not the metric)"
     parity_ok = True
-    if world > 1 or args.shard_of > 1:
-        out["parity_distributed"] = dist_check
-        parity_ok = dist_check["ok"]
-    if world == 1 and not args.no_e2e:
-        out["e2e"] = end_to_end(eng, table, names, lens, buf, offs, local, stream)
-    if world == 1 and args.e2e_file:
-        out["e2e_file"] = end_to_end_file(eng._sts_path, names, lens, buf, offs, cfg, local)
-    if world == 1 and not args.no_cpu_baseline and args.shard_of <= 1:
-        hits = search.fetch(nhits)
-        threads = args.cpu_threads or host_cores()
-        out["cpu_baseline"], otable, oprm = cpu_baseline(eng, lens, buf, offs, cfg, hits, args.cpu_budget, threads)
-        parity_ok = out["cpu_baseline"]["parity_vs_gpu"]
-        if not args.no_ref_model:
-            out["cpu_baseline_reference_model"] = reference_model(otable, oprm, buf, offs, lens, threads,
-                                                                  args.cpu_budget)
+    if args.full:
+        kern_ev_s = float(np.mean(scan_ms)) / 1e3  # HIP events on the scan's launch stream
+        alg_bytes = BYTES_PER_BASE * st["windows"] + BYTES_PER_HIT * search.last_hits()  # rank 0's scan launch
+        # the scan stage's kernels (events around all of them): a split W 7..9 table scans its two
+        # exact seeds with scan_kernel (plus dense_kernel over the records they cannot carry)
+        sp = table.split()
+        if sp["seed_tables"]:
+            W = cfg["W"]
+            scan_label = (f"mp::scan_kernel x{sp['seed_tables']} (split seeds: exact [0, 11)"
+                          + (f" + gapped [0, {W}) ++ [11, {22 - W})" if sp["seed_tables"] > 1 else "")
+                          + (f" + dense_kernel over {sp['rest_records']} records" if sp["rest_records"] else "")
+                          + "; one stage, HIP events around all of it)")
+        else:
+            scan_label = "mp::dense_kernel" if cfg["W"] <= 9 else "mp::scan_kernel"
+        # roofline.traffic / issue: counters measured now, in child passes of this very command;
+        # failing that, a committed profile of this same build; else null with the reason
+        pmc, pmc_src, traffic, why = None, None, None, "not measured for N > 1 or shard runs"
+        if world == 1 and args.shard_of <= 1:
+            regex = "scan_kernel|dense_kernel" if (sp["seed_tables"] or cfg["W"] <= 9) else "scan_kernel"
+            live, why = (None, "--no-pmc") if args.no_pmc else live_pmc(sys.argv[1:], regex)
+            if live is not None:
+                pmc, pmc_src = live, why
+                traffic = 2.0 * live["FETCH_SIZE"] * 1024 + live["WRITE_SIZE"] * 1024
+            else:
+                log(f"live counters unavailable ({why}); looking for a committed profile of build {build}")
+                prof, tag = pmc_profile(workload, build)
+                if prof is not None:
+                    pmc, pmc_src = prof, f"profiles/{tag}_pmc.json (committed profile of this build)"
+                    traffic = prof["hbm_traffic_bytes_per_launch"]
+        kern_s, kern_src = roofline_time(pmc, kern_ev_s)
+        achieved = alg_bytes / kern_s / 1e9 if kern_s > 0 else 0.0
+        out.update({
+            "single_run_ms": round(single_ms, 3) if single_ms is not None else None,
+            "scan_kernel_ms": round(kern_s * 1e3, 3),
+            "scan_kernel_ms_source": kern_src,
+            "scan_kernel_ms_events": round(kern_ev_s * 1e3, 3),
+            "tail_kernel_ms": round(float(np.mean(tail_ms)), 3),
+            "pair_kernel_ms": round(float(np.mean(pair_ms)), 3),
+            "order_ms": round(float(np.mean(order_ms)), 3),
+            "survivors": st["survivors"],
+            "kernel_gbps_bases": round(st["windows"] / kern_s / 1e9, 3) if kern_s > 0 else None,
+            "candidates": st["candidates"],
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 5),
+                         "traffic": int(traffic) if traffic else None,
+                         "traffic_source": (pmc_src + "; 2 x FETCH_SIZE KiB (gfx950 half-count) + WRITE_SIZE KiB, "
+                                            "Infinity-Cache hits included") if traffic else None,
+                         "traffic_null_reason": None if traffic else why,
+                         "kernel": scan_label,
+                         "alg_bytes_per_launch": int(alg_bytes),
+                         "time_ms": round(kern_s * 1e3, 4),
+                         "time_source": kern_src,
+                         "trace_forms": (pmc or {}).get("_trace_forms"),
+                         "issue": (dict(issue_bound(pmc, kern_s * 1e9), source=pmc_src) if pmc else None)},
+            "single_run_note": "one isolated search (enqueue -> complete, host turnaround included) on one handle, "
+                               "median of 5 after the timed steps; ms_per_step is the pipelined throughput",
+            "scan_timing": ("HIP events around the scan kernel on its launch stream in every timed step"
+                            if scan_in_timed else
+                            "HIP events around the scan kernel on its launch stream in 3 untimed steps after the "
+                            "timed ones, run one at a time (in the timed steps kernels of consecutive steps overlap)"),
+        })
+        if world > 1 or args.shard_of > 1:
+            out["parity_distributed"] = dist_check
+            parity_ok = dist_check["ok"]
+        if world == 1 and not args.no_e2e:
+            out["e2e"] = end_to_end(eng, table, names, lens, buf, offs, local, stream)
+        if world == 1 and args.e2e_file:
+            out["e2e_file"] = end_to_end_file(eng._sts_path, names, lens, buf, offs, cfg, local)
+        if world == 1 and not args.no_cpu_baseline and args.shard_of <= 1:
+            hits = search.fetch(nhits)
+            threads = args.cpu_threads or host_cores()
+            out["cpu_baseline"], otable, oprm = cpu_baseline(eng, lens, buf, offs, cfg, hits, args.cpu_budget, threads)
+            parity_ok = out["cpu_baseline"]["parity_vs_gpu"]
+            if not args.no_ref_model:
+                out["cpu_baseline_reference_model"] = reference_model(otable, oprm, buf, offs, lens, threads,
+                                                                      args.cpu_budget)
     print(json.dumps(out), flush=True)
     if world > 1:
         if comm is not None:

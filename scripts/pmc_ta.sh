@@ -11,7 +11,7 @@ Q="--no-cpu-baseline --no-e2e --steps 2 --warmup 1 $*"
 run() {
   local name=$1; shift
   timeout -s KILL 240 rocprofv3 --pmc "$@" --kernel-include-regex "$KRE" -d "$OUT/$name" -o run --output-format csv \
-      -- python3 "$R/bench.py" $Q > "$OUT/$name.log" 2>&1 || { echo "pass $name failed rc=$?"; tail -5 "$OUT/$name.log"; exit 1; }
+      -- python3 "$R/bench.py" --full $Q > "$OUT/$name.log" 2>&1 || { echo "pass $name failed rc=$?"; tail -5 "$OUT/$name.log"; exit 1; }
   echo "pass $name ok"
 }
 run ta1 TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum GRBM_GUI_ACTIVE

@@ -10,7 +10,7 @@ run() {  # name, bench-args
   local OUT=$R/gpurun_out/prof_$1; shift
   mkdir -p "$OUT"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-      -- python3 "$R/bench.py" "$@" > "$OUT/trace.log" 2>&1 \
+      -- python3 "$R/bench.py" --full "$@" > "$OUT/trace.log" 2>&1 \
       || { echo "trace $OUT failed rc=$?"; tail -5 "$OUT/trace.log"; exit 1; }
   echo "trace $OUT ok"; tail -1 "$OUT/trace.log"
 }

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 run() {  # name, bench-args, rocprof args...
   local name=$1; local bargs=$2; shift 2
-  timeout -k 10 400 rocprofv3 "$@" -d "$OUT/$name" -o run --output-format csv -- python3 "$R/bench.py" $bargs \
+  timeout -k 10 400 rocprofv3 "$@" -d "$OUT/$name" -o run --output-format csv -- python3 "$R/bench.py" --full $bargs \
       > "$OUT/$name.log" 2>&1 || { echo "pass $name failed rc=$?"; tail -5 "$OUT/$name.log"; exit 1; }
   echo "pass $name ok"
 }

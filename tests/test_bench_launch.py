@@ -55,6 +55,47 @@ def test_mismatch_exits_before_any_gpu_work():
     assert "WORLD_SIZE=2" in r.stderr
 
 
+def test_dump_outputs_writes_the_hit_list_field_by_field(tmp_path):
+    """--dump-outputs: one float64 .npy per field of the hit list, in list order, and its length;
+    a list too long for the byte budget is cut to the same seeded rows every time."""
+    import numpy as np
+    from merpcr_amd._native import HIT_DTYPE
+    hits = np.zeros(1000, dtype=HIT_DTYPE)
+    hits["pos1"] = np.arange(1000, dtype=np.uint64) * 3_000_017 + (1 << 40)
+    hits["pos2"] = hits["pos1"] + 200
+    hits["seq"] = np.arange(1000) % 24
+    hits["rec"] = np.arange(1000)[::-1]
+    d = tmp_path / "whole"
+    bench.dump_outputs(str(d), hits)
+    assert sorted(os.listdir(d)) == ["hits_pos1.npy", "hits_pos2.npy", "hits_rec.npy", "hits_seq.npy", "n_hits.npy"]
+    for f in HIT_DTYPE.names:
+        a = np.load(d / f"hits_{f}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a.astype(np.uint64), hits[f])
+    assert np.load(d / "n_hits.npy").tolist() == [1000.0]
+    # 100 rows fit: 8 bytes for the length, 5 float64 per row (4 fields and the row's index)
+    small = [tmp_path / "s1", tmp_path / "s2"]
+    for s in small:
+        bench.dump_outputs(str(s), hits, max_bytes=8 + 100 * 40)
+    idx = np.load(small[0] / "hits_index.npy")
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and idx[-1] < 1000
+    assert np.load(small[0] / "n_hits.npy").tolist() == [1000.0]
+    total = 0
+    for f in sorted(os.listdir(small[0])):
+        a, b = np.load(small[0] / f), np.load(small[1] / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 8 + 100 * 40
+    assert np.array_equal(np.load(small[0] / "hits_pos1.npy"), hits["pos1"][idx.astype(np.int64)].astype(np.float64))
+
+
+def test_counter_passes_drop_the_callers_extras():
+    """live_pmc's child passes keep the workload options and drop step counts, --full and the dump."""
+    got = bench.pmc_child_args(["--gpus", "1", "--full", "--config", "c4", "--dump-outputs", "d", "--steps=7",
+                                "--no-e2e", "--scale", "0.5"])
+    assert got[:4] == ["--config", "c4", "--scale", "0.5"]
+    assert "--full" not in got and "--dump-outputs" not in got and "d" not in got and "--pmc-child" in got
+
+
 def test_trace_stage_time_filters_the_scan_forms(tmp_path):
     """roofline's time: the kernel-trace pass holds every kernel of the child process; only the
     scan stage's forms count, each averaged without its first (cold) dispatch, forms summed."""
