@@ -231,6 +231,36 @@ int mp_search_survivors(void* search, uint64_t* n_survivors);
 int mp_search_timing(void* search, float* scan_ms, float* tail_ms, float* pair_ms, float* order_ms);
 void mp_search_destroy(void* search);
 
+/* ---- per-hit details (what classic e-PCR output adds to a hit: the mismatches of each
+ * primer, engine.py:599-642 counted instead of capped, and the product itself) ----------
+ * Both calls work on hits [first, first + count) of the handle's last completed run, in its
+ * output order, and read only what that run left on the device: the sorted hit list, the
+ * genome planes and the table's primers.  MP_E_STATE when no run has completed on the
+ * handle, when one is enqueued, or when the genome was reset or put into since the run;
+ * MP_E_ARG when first + count exceeds the run's hits.  count == 0 succeeds without touching
+ * the device.  Their device scratch is allocated at first use, kept on the handle and
+ * counted by mp_search_dev_bytes from then on.  Both wait for their result. */
+typedef struct mp_hit_info {
+    uint8_t mm1;  /* mismatching positions of primer 1 against [pos1, pos1 + l1) */
+    uint8_t mm2;  /* ... of primer 2 against [pos2 + 1 - l2, pos2 + 1) */
+} mp_hit_info;
+/* The per-position rule is _compare_seqs' (accept planes; under I = 1 a genome 'N' matches
+ * every IUPAC primer base; other non-ACGT genome characters are compared as characters;
+ * bytes >= 0x80 match only themselves), with no N cap and no 3' exit: every position is
+ * counted, so a hit's counts are <= N.  host_out: count entries. */
+int mp_search_annotate(void* search, uint64_t first, uint64_t count, mp_hit_info* host_out, void* stream);
+/* Upper-cased text [pos1, pos2] of each hit's sequence, concatenated into host_out:
+ * amplicon i is bytes [off[i], off[i + 1]).  off[count + 1] is always filled and
+ * *n_bytes = off[count], the size needed; host_out == NULL is a size query; cap < need fails
+ * with MP_E_CAP and nothing is written to host_out.  A non-ACGT base comes out as the
+ * character that was put ('N', IUPAC letters, 'U', opaque bytes >= 0x80), upper-cased. */
+int mp_search_amplicons(void* search, uint64_t first, uint64_t count, uint8_t* host_out, uint64_t cap,
+                        uint64_t* off, uint64_t* n_bytes, void* stream);
+/* Device time of the last mp_search_annotate's kernel and of the last filling
+ * mp_search_amplicons' kernels (lengths, offsets scan, text), by HIP events; -1 before the
+ * first such call. */
+int mp_search_detail_timing(void* search, float* annotate_ms, float* amplicon_ms);
+
 /* ---- multi-GPU (replaces the -T ProcessPool fan-out over chunks of a record,
  * engine.py:386-422) --------------------------------------------------
  * One process, several devices: the genome's (sequence, k) space is split into owned
@@ -373,6 +403,23 @@ int mp_format_hits(const mp_hit* hits, uint64_t n_hits,
                    const uint8_t* labels, const uint64_t* label_off, uint32_t n_seq,
                    const uint8_t* rec_text, const uint64_t* rec_off, uint32_t n_rec,
                    uint8_t* out, uint64_t cap, uint64_t* n_bytes);
+/* mp_format_hits with three more columns per line:
+ *     "{label}\t{pos1+1}..{pos2+1}\t{rec_text}\t{mm1}\t{mm2}\t{size}/{expected}\n"
+ * info[i] belongs to hits[i] (mp_search_annotate), size = pos2 - pos1 + 1 and expected =
+ * pcr_size[rec] (n_rec entries, the table's). */
+int mp_format_hits_ex(const mp_hit* hits, uint64_t n_hits,
+                      const uint8_t* labels, const uint64_t* label_off, uint32_t n_seq,
+                      const uint8_t* rec_text, const uint64_t* rec_off, uint32_t n_rec,
+                      const mp_hit_info* info, const uint64_t* pcr_size,
+                      uint8_t* out, uint64_t cap, uint64_t* n_bytes);
+/* The hits' amplicons as FASTA, one record per hit:
+ *     ">{label}:{pos1+1}..{pos2+1}\t{rec_text}\n{bases}\n"
+ * bases / off: mp_search_amplicons' output for the same hits (off[n_hits + 1]). */
+int mp_format_amplicons(const mp_hit* hits, uint64_t n_hits,
+                        const uint8_t* labels, const uint64_t* label_off, uint32_t n_seq,
+                        const uint8_t* rec_text, const uint64_t* rec_off, uint32_t n_rec,
+                        const uint8_t* bases, const uint64_t* off,
+                        uint8_t* out, uint64_t cap, uint64_t* n_bytes);
 
 #ifdef __cplusplus
 }

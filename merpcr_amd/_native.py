@@ -35,6 +35,7 @@ EXPORTS = (
     "mp_search_create", "mp_search_set_options", "mp_search_set_stage_timing", "mp_search_set_scan_timing", "mp_search_run",
     "mp_search_enqueue", "mp_search_complete", "mp_search_fetch", "mp_search_fetch_device", "mp_search_device_hits",
     "mp_search_last_stats", "mp_search_regrowths", "mp_search_dev_bytes", "mp_search_survivors", "mp_search_timing", "mp_search_destroy",
+    "mp_search_annotate", "mp_search_amplicons", "mp_search_detail_timing",
     "mp_multi_create", "mp_multi_genome", "mp_multi_put", "mp_multi_seal", "mp_multi_run", "mp_multi_fetch",
     "mp_multi_set_gather", "mp_multi_device_search", "mp_multi_timing", "mp_multi_destroy",
     "mp_comm_unique_id", "mp_comm_create", "mp_comm_gather_hits", "mp_comm_destroy",
@@ -42,7 +43,7 @@ EXPORTS = (
     "mp_fasta_load", "mp_fasta_load_parallel", "mp_fasta_load_chunked", "mp_fasta_info", "mp_fasta_record_ascii", "mp_fasta_record", "mp_fasta_destroy",
     "mp_fasta_load_device", "mp_fasta_device_info", "mp_fasta_device_record", "mp_fasta_device_read",
     "mp_fasta_device_destroy",
-    "mp_format_hits",
+    "mp_format_hits", "mp_format_hits_ex", "mp_format_amplicons",
     "mp_sts_parse", "mp_sts_info", "mp_sts_arrays", "mp_sts_record_texts", "mp_sts_destroy",
 )
 
@@ -80,6 +81,10 @@ MP_GATHER = {"copy": 0, "rccl": 1}
 
 
 HIT_DTYPE = np.dtype([("pos1", "<u8"), ("pos2", "<u8"), ("seq", "<u4"), ("rec", "<u4")])
+
+
+class MPHitInfo(ctypes.Structure):
+    _fields_ = [("mm1", c_uint8), ("mm2", c_uint8)]
 
 
 class NativeError(RuntimeError):
@@ -149,6 +154,9 @@ def _sig(lib):
     lib.mp_search_timing.argtypes = [P, POINTER(c_float), POINTER(c_float), POINTER(c_float), POINTER(c_float)]
     lib.mp_search_destroy.argtypes = [P]
     lib.mp_search_destroy.restype = None
+    lib.mp_search_annotate.argtypes = [P, c_uint64, c_uint64, P, P]
+    lib.mp_search_amplicons.argtypes = [P, c_uint64, c_uint64, P, c_uint64, P, u64p, P]
+    lib.mp_search_detail_timing.argtypes = [P, POINTER(c_float), POINTER(c_float)]
     lib.mp_multi_create.argtypes = [c_uint32, POINTER(c_int32), POINTER(c_void_p), POINTER(c_void_p)]
     lib.mp_multi_genome.argtypes = [P, c_uint32, P]
     lib.mp_multi_put.argtypes = [P, c_uint32, P, c_uint64]
@@ -190,6 +198,8 @@ def _sig(lib):
     lib.mp_sts_destroy.argtypes = [P]
     lib.mp_sts_destroy.restype = None
     lib.mp_format_hits.argtypes = [P, c_uint64, P, P, c_uint32, P, P, c_uint32, P, c_uint64, u64p]
+    lib.mp_format_hits_ex.argtypes = [P, c_uint64, P, P, c_uint32, P, P, c_uint32, P, P, P, c_uint64, u64p]
+    lib.mp_format_amplicons.argtypes = [P, c_uint64, P, P, c_uint32, P, P, c_uint32, P, P, P, c_uint64, u64p]
 
 
 def _share_hip_runtime():
@@ -477,6 +487,41 @@ class Search:
         check(lib().mp_search_timing(self._h, ctypes.byref(t1), ctypes.byref(t0), ctypes.byref(t2), ctypes.byref(t3)))
         return {"scan_ms": ms.value, "windows": nw.value, "candidates": nc.value, "survivors": sv.value,
                 "tail_ms": t0.value, "pair_ms": t2.value, "order_ms": t3.value}
+
+    def _window(self, first, count):
+        first = int(first)
+        if count is None:
+            count = max(0, self.last_hits() - first)
+        return first, int(count)
+
+    def annotate(self, first: int = 0, count=None, stream=None) -> np.ndarray:
+        """uint8[n, 2]: the mismatching positions of primer 1 and primer 2 for hits
+        [first, first + count) of the last completed run (mp_search_annotate); count None =
+        every hit from `first` on."""
+        first, count = self._window(first, count)
+        out = np.empty((count, 2), dtype=np.uint8)
+        check(lib().mp_search_annotate(self._h, first, count, ptr(out), c_void_p(stream or 0)))
+        return out
+
+    def amplicons(self, first: int = 0, count=None, stream=None):
+        """(bytes_u8, off_u64) of the same window (mp_search_amplicons): amplicon i is
+        bytes_u8[off[i]:off[i + 1]], the upper-cased sequence text [pos1, pos2].  A size query,
+        then the fill."""
+        first, count = self._window(first, count)
+        off = np.zeros(count + 1, dtype=np.uint64)
+        n = c_uint64(0)
+        s = c_void_p(stream or 0)
+        check(lib().mp_search_amplicons(self._h, first, count, None, 0, ptr(off), ctypes.byref(n), s))
+        out = np.empty(n.value, dtype=np.uint8)
+        if n.value:
+            check(lib().mp_search_amplicons(self._h, first, count, ptr(out), out.size, ptr(off), ctypes.byref(n), s))
+        return out, off
+
+    def detail_timing(self):
+        """Device ms of the last annotate's kernel and the last amplicons fill's kernels."""
+        a, b = c_float(), c_float()
+        check(lib().mp_search_detail_timing(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return {"annotate_ms": a.value, "amplicon_ms": b.value}
 
     def close(self):
         if self._h:
@@ -819,12 +864,36 @@ class Formatter:
             self.rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
         self.n_seq, self.n_rec = len(labels), len(self.rec_off) - 1
 
-    def __call__(self, hits: np.ndarray) -> bytes:
-        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    def _run(self, fn, hits, *extra) -> bytes:
+        """Size query, then the fill, of one of the mp_format_* calls."""
         n = c_uint64()
         args = (ptr(hits), hits.size, ptr(self.labels), ptr(self.label_off), self.n_seq,
-                ptr(self.rec), ptr(self.rec_off), self.n_rec)
-        check(lib().mp_format_hits(*args, None, 0, ctypes.byref(n)))
+                ptr(self.rec), ptr(self.rec_off), self.n_rec) + extra
+        check(fn(*args, None, 0, ctypes.byref(n)))
         out = np.empty(n.value, dtype=np.uint8)
-        check(lib().mp_format_hits(*args, ptr(out), out.size, ctypes.byref(n)))
+        check(fn(*args, ptr(out), out.size, ctypes.byref(n)))
         return out.tobytes()
+
+    def __call__(self, hits: np.ndarray) -> bytes:
+        return self._run(lib().mp_format_hits, np.ascontiguousarray(hits, dtype=HIT_DTYPE))
+
+    def detailed(self, hits: np.ndarray, info: np.ndarray, pcr_size: np.ndarray) -> bytes:
+        """The hit lines with "\t{mm1}\t{mm2}\t{size}/{expected}" appended (mp_format_hits_ex):
+        info = Search.annotate's uint8[n, 2] for the same hits, pcr_size = each record's
+        expected size."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        info = np.ascontiguousarray(info, dtype=np.uint8)
+        pcr_size = np.ascontiguousarray(pcr_size, dtype=np.uint64)
+        if info.shape != (hits.size, 2) or pcr_size.size != self.n_rec:
+            raise ValueError("detailed(): info must be uint8[n_hits, 2] and pcr_size one entry per record")
+        return self._run(lib().mp_format_hits_ex, hits, ptr(info), ptr(pcr_size))
+
+    def amplicons(self, hits: np.ndarray, bases: np.ndarray, off: np.ndarray) -> bytes:
+        """The hits' amplicons as FASTA (mp_format_amplicons): ">{label}:{pos1+1}..{pos2+1}\t{rec_text}"
+        and the bases; bases / off = Search.amplicons' result for the same hits."""
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if off.size != hits.size + 1 or (off.size and int(off[-1]) > bases.size):
+            raise ValueError("amplicons(): off must hold n_hits + 1 offsets into bases")
+        return self._run(lib().mp_format_amplicons, hits, ptr(bases), ptr(off))

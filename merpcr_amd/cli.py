@@ -96,6 +96,11 @@ def create_parser() -> argparse.ArgumentParser:
     p.add_argument("--emulate-chunks", action="store_true",
                    help="with -T > 1, reproduce the reference's per-chunk output (duplicate overlap "
                         "hits) instead of the exact single-chunk result")
+    p.add_argument("--details", action="store_true",
+                   help="append to every hit line the mismatches of each primer and the observed/expected "
+                        "product size: <mm1> <mm2> <size>/<expected> (tab-separated)")
+    p.add_argument("--amplicons", metavar="FILE", type=str, default=None,
+                   help="write every hit's product sequence to FILE as FASTA")
     return p
 
 
@@ -138,7 +143,7 @@ def main(argv: List[str] = None) -> int:
         if not records:
             logger.error(f"Failed to load FASTA file: {args.fasta_file}")
             return 1
-        n = eng.search(records, args.output)
+        n = eng.search(records, args.output, details=args.details, amplicon_file=args.amplicons)
         logger.info(f"Search complete: {n} hits found")
         return 0
     except Exception as e:  # cli.py:260-266: any failure -> exit 1

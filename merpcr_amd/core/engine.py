@@ -185,6 +185,33 @@ class _NativeRecords:
         return self._blob
 
 
+class HitDetails:
+    """What find_hits_detailed returns: the hits of find_hits plus, per hit, the mismatching
+    positions of each primer (mm1, mm2), the product's size (pos2 - pos1 + 1), the record's
+    expected size, and -- when asked for -- the amplicon text."""
+
+    def __init__(self, hits, mm, expected, records, amp=None):
+        self.hits = hits
+        self.mm1 = np.ascontiguousarray(mm[:, 0])
+        self.mm2 = np.ascontiguousarray(mm[:, 1])
+        self.size = (hits["pos2"] - hits["pos1"] + 1).astype(np.uint64)
+        self.expected = expected
+        self._records = records
+        self._amp = amp  # (bytes_u8, off_u64) of _native.Search.amplicons, or None
+
+    def __len__(self):
+        return len(self.hits)
+
+    def amplicon(self, i: int) -> str:
+        """Hit i's product: ``sequence.upper()[pos1:pos2 + 1]`` of its record.  Decoded from the
+        device's bytes, except for a record whose sequence is a non-ASCII host string: there
+        the device holds opaque codes and the host string is sliced instead."""
+        if self._amp is None:
+            raise ValueError("amplicons were not requested (find_hits_detailed(..., amplicons=True))")
+        h = self.hits[i]
+        return _amplicon_text(self._records[int(h["seq"])], h, *self._amp, i)
+
+
 class MerPCR:
     """Electronic-PCR STS search (reference: core/engine.py:44)."""
 
@@ -648,6 +675,33 @@ class MerPCR:
         self.device_table()  # registers the primers' non-ASCII codes before the genome is encoded
         return self._hits_of(self.encode_records(fasta_records))
 
+    def _check_details(self):
+        """Per-hit details read one device's resident planes and its run's own hit list."""
+        if len(self.devices) > 1:
+            raise ValueError("per-hit details are not available on a multi-device engine (devices > 1)")
+        if self.emulate_chunks and self.threads > 1:
+            raise ValueError("per-hit details are not available with emulate_chunks and threads > 1")
+
+    def _pcr_sizes(self) -> np.ndarray:
+        """Each record's expected size, from where _table_arrays takes it."""
+        if self._native_current():
+            return self._native_arrays[2][2]
+        recs = self._recs
+        return np.fromiter((r.pcr_size for r in recs), dtype=np.uint64, count=len(recs))
+
+    def find_hits_detailed(self, fasta_records: Sequence[FASTARecord], amplicons: bool = False) -> HitDetails:
+        """find_hits plus each hit's primer mismatch counts, observed and expected size and
+        (amplicons=True) product text, computed on the GPU from the planes the search left
+        resident (mp_search_annotate / mp_search_amplicons).  One device, no chunk emulation."""
+        self._check_details()
+        recs = list(fasta_records)
+        self.device_table()
+        hits = self._search_device(self.encode_records(recs))
+        mm = self._dev_search.annotate()
+        amp = self._dev_search.amplicons() if amplicons else None
+        expected = self._pcr_sizes()[hits["rec"].astype(np.int64)] if len(hits) else np.zeros(0, dtype=np.uint64)
+        return HitDetails(hits, mm, expected, recs, amp)
+
     def _hits_of(self, data: List[np.ndarray]) -> np.ndarray:
         if not (self.emulate_chunks and self.threads > 1):
             return self._search_device(data)
@@ -755,10 +809,28 @@ class MerPCR:
             t -= 1
             logger.info(f"Reduced threads to {t} due to sequence size limitations")
 
+    def _formatter(self, fasta_records: Sequence[FASTARecord]):
+        from .. import _native
+        return _native.Formatter([r.label for r in fasta_records], *self._record_texts())
+
     def format_bytes(self, fasta_records: Sequence[FASTARecord], hits: np.ndarray) -> bytes:
         """The output text of engine.py:437-443 for `hits`, UTF-8, by mp_format_hits."""
-        from .. import _native
-        return _native.Formatter([r.label for r in fasta_records], *self._record_texts())(hits)
+        return self._formatter(fasta_records)(hits)
+
+    def _write_amplicons(self, path: str, recs: Sequence[FASTARecord], hits: np.ndarray):
+        """Every hit's product as FASTA (mp_format_amplicons) from the device's bytes; the hits
+        of a non-ASCII host string are re-cut from that string (HitDetails.amplicon)."""
+        if not len(hits):
+            open(path, "w").close()
+            return
+        data, off = self._dev_search.amplicons()
+        if any(_opaque_on_device(r) for r in recs):
+            parts = [_amplicon_text(recs[int(h["seq"])], h, data, off, i).encode("utf-8") for i, h in enumerate(hits)]
+            off = np.zeros(len(hits) + 1, dtype=np.uint64)
+            np.cumsum([len(b) for b in parts], out=off[1:])
+            data = np.frombuffer(b"".join(parts), dtype=np.uint8)
+        with open(path, "wb") as f:
+            f.write(self._formatter(recs).amplicons(hits, data, off))
 
     def _record_texts(self):
         """The formatter's record column (UTF-8 "id\talias\t(direct)" per record, and
@@ -779,13 +851,22 @@ class MerPCR:
         recs = self.sts_records
         return [STSHit(pos1=int(h["pos1"]), pos2=int(h["pos2"]), sts=recs[int(h["rec"])]) for h in hits]
 
-    def search(self, fasta_records: List[FASTARecord], output_file: str = None) -> int:
+    def search(self, fasta_records: List[FASTARecord], output_file: str = None, *, details: bool = False,
+               amplicon_file: str = None) -> int:
         """Search every record; print one line per hit (engine.py:365-451).
+
+        details=True appends "\t{mm1}\t{mm2}\t{size}/{expected}" to every line (the mismatching
+        positions of each primer, the product's size and the record's expected size);
+        amplicon_file receives every hit's product as FASTA
+        (">{label}:{pos1+1}..{pos2+1}\t{id}\t{alias}\t({direct})").  Both are computed on the GPU
+        after the search; without them the output is the reference's, byte for byte.
 
         One device pass covers all records; the per-record log lines and output then follow
         in the reference's order (record i's lines before record i+1's log).  A record the
         reference's scan would fail on (IndexError, see encode_sequences) ends the call
         after the output of the records before it, as in the reference."""
+        if details or amplicon_file:
+            self._check_details()
         to_file = bool(output_file) and output_file.lower() != "stdout"
         output = open(output_file, "w") if to_file else sys.stdout
         total = 0
@@ -806,7 +887,13 @@ class MerPCR:
                                "multi-process chunking repeats hits inside chunk overlaps; "
                                "emulate_chunks=True reproduces that output)")
             hits = self._hits_of(data) if n_ok else np.zeros(0, dtype=_hit_dtype())
-            text = self.format_bytes(recs[:n_ok], hits) if len(hits) else b""
+            text = b""
+            if len(hits) and details:
+                text = self._formatter(recs[:n_ok]).detailed(hits, self._dev_search.annotate(), self._pcr_sizes())
+            elif len(hits):
+                text = self.format_bytes(recs[:n_ok], hits)
+            if amplicon_file:
+                self._write_amplicons(amplicon_file, recs[:n_ok], hits)
             # byte range of each record's lines: hits are ordered by record
             per = np.bincount(hits["seq"].astype(np.int64), minlength=n_ok) if len(hits) else np.zeros(n_ok, np.int64)
             ends = np.flatnonzero(np.frombuffer(text, dtype=np.uint8) == 10) + 1 if text else np.zeros(0, np.int64)
@@ -853,6 +940,20 @@ def _raw_ascii(rec):
 def _device_span(rec):
     f = getattr(rec, "device_span", None)
     return f() if f is not None else None
+
+
+def _opaque_on_device(rec) -> bool:
+    """The record went to the device as a non-ASCII host string: its device bytes hold opaque
+    codes (CharCodes) where the characters are not ASCII."""
+    return _device_span(rec) is None and _raw_ascii(rec) is None and not rec.sequence.isascii()
+
+
+def _amplicon_text(rec, hit, data, off, i) -> str:
+    """Hit i's product from the device's bytes (data, off: _native.Search.amplicons), or from
+    the host string where those bytes are opaque codes."""
+    if _opaque_on_device(rec):
+        return rec.sequence.upper()[int(hit["pos1"]):int(hit["pos2"]) + 1]
+    return data[int(off[i]):int(off[i + 1])].tobytes().decode("latin-1")
 
 
 def _seq_len(rec) -> int:

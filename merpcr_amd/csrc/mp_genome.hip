@@ -241,6 +241,7 @@ static int put_device_bytes(Genome* g, uint32_t seq, uint64_t offset, const uint
         return fail(MP_E_ARG, "mp_genome_put: non-final chunk must be a multiple of 64 bytes");
     if (!nbytes) return MP_OK;
     g->sealed = false;
+    ++g->gen;
     const uint64_t tiles = (nbytes + kPackTile - 1) / kPackTile;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((tiles + 3) / 4, 8192);  // 4 waves per block
     // first pass: pack + count runs; grow the run index and redo on overflow
@@ -321,6 +322,7 @@ static int place(Genome* g) {
     g->n_xr = 0;
     g->has_u = false;
     g->sealed = false;
+    ++g->gen;
     return grow_runs(g, 1 << 16);
 }
 

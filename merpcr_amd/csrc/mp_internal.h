@@ -236,6 +236,8 @@ struct Genome {
     uint64_t plane_cap = 0;   // padded bases the planes hold
     uint32_t seq_cap = 0;     // sequences d_base / d_len hold
     uint32_t n_pending = 0;   // search runs enqueued over this genome and not yet completed
+    uint64_t gen = 0;         // content generation: bumped by every reset and put (a search records it at
+                              // completion; `sealed` cannot tell a refilled genome from the one searched)
 };
 
 struct Search {
@@ -294,6 +296,11 @@ struct Search {
     uint64_t pend_tiles = 0;                // super-steps of the enqueued run
     int pend_mode = 0;                      // its order mode
     alignas(16) unsigned char pend_args[640];  // its ScanArgs (mp_search.hip)
+    // per-hit details of the last completed run (mp_detail.hip)
+    bool has_run = false;                   // a run has completed and its sorted list is in `out`
+    uint64_t run_gen = 0;                   // Genome::gen at that completion
+    struct Detail* detail = nullptr;        // scratch of the detail calls, allocated at their first use
+    uint64_t detail_bytes = 0;              // its device bytes (0 for a handle that never asked)
 };
 
 // ---------------------------------------------------------------- device helpers
@@ -684,5 +691,6 @@ __device__ __forceinline__ void finish_fold(unsigned long long* __restrict__ cou
     }
 }
 int sort_runs(Genome* g, hipStream_t st);
+void free_detail(Search* s);  // the detail calls' scratch (mp_detail.hip), with the handle
 
 }  // namespace mp

@@ -2627,6 +2627,7 @@ static void free_search(Search* s) {
         delete[] s->put_ev;
     }
     if (s->put_done) hipEventDestroy(s->put_done);
+    free_detail(s);
     delete s;
 }
 
@@ -2698,6 +2699,7 @@ MP_EXPORT int mp_search_set_options(void* search, const mp_search_options* opt) 
         return fail(MP_E_ARG, "mp_search_set_options: option out of range");
     MP_HIP_CHECK(hipSetDevice(s->genome->device));
     s->opt = *opt;
+    s->has_run = false;  // the hit list is reallocated below
     s->order_mode = opt->sort == MP_SORT_SCATTER ? 1 : 0;
     int rc = alloc_hits(s, opt->hit_cap ? opt->hit_cap : kDefaultHitCap);
     if (!rc) rc = alloc_surv(s, opt->surv_cap ? opt->surv_cap : kDefaultSurvCap);
@@ -3305,14 +3307,20 @@ MP_EXPORT int mp_search_complete(void* search, uint64_t* n_hits) {
     // handle and its genome locked in MP_E_STATE); a failure marks the counters dirty
     if (n_hits) *n_hits = 0;
     s->pending = false;
+    s->has_run = false;
     if (s->genome->n_pending) --s->genome->n_pending;
-    if (s->pend_empty) return MP_OK;
+    s->run_gen = s->genome->gen;  // what the detail calls (mp_detail.hip) may read the planes for
+    if (s->pend_empty) {
+        s->has_run = true;
+        return MP_OK;
+    }
     if (hipSetDevice(s->genome->device) != hipSuccess) {
         s->dirty = true;
         MP_HIP_CHECK(hipSetDevice(s->genome->device));
     }
     const int rc = search_complete(s, n_hits);
     if (rc) s->dirty = true;
+    s->has_run = rc == MP_OK;
     return rc;
 }
 
@@ -3369,7 +3377,7 @@ MP_EXPORT int mp_search_dev_bytes(void* search, uint64_t* dev_bytes) {
     Search* s = (Search*)search;
     if (!s || !dev_bytes) return fail(MP_E_ARG, "mp_search_dev_bytes: null pointer");
     *dev_bytes = s->cap * (16 + 8 + 8 + sizeof(mp_hit)) + s->surv_cap * sizeof(uint4) + s->tails_cap * 2 * sizeof(uint4) +
-                 s->spans_cap * sizeof(SeqSpan) + s->slots_bytes + s->sort_tmp_bytes + kCounterBytes;
+                 s->spans_cap * sizeof(SeqSpan) + s->slots_bytes + s->sort_tmp_bytes + kCounterBytes + s->detail_bytes;
     return MP_OK;
 }
 
