@@ -5,6 +5,13 @@ Run only in the build container, where the reference is importable:
     PYTHONPATH=/root/reference/src python3 tests/golden/make_golden.py
     PYTHONPATH=/root/reference/src python3 tests/golden/make_golden.py --chunked   # -T N corpus
     PYTHONPATH=/root/reference/src python3 tests/golden/make_golden.py --errors    # error paths
+    ... make_golden.py --wide      # W >= 14, long primers, wide margins
+
+Fixtures: bundled, repeat, random_cases, special_cases, threaded, unit_kats (.json.gz, the
+plain run), chunked.json.gz (--chunked), errors.json.gz (--errors) and wide.json.gz (--wide:
+65 planted cases at W 14/15/16 and 8/11, primers of W to 130 bases, margins 51 to 10,000, with
+the list of what was planted where; its tally goes to stderr and tests/test_oracle_golden.py
+asserts it).
 
 The reference never ships with this repository and never runs on the GPU box;
 what is committed is data only: the seeded inputs each case was built from and
@@ -467,7 +474,334 @@ def chunked_cases():
     return out
 
 
+# --------------------------------------------------------------------------
+# --wide: hashed tables (W >= 14), long primers, wide margins
+# --------------------------------------------------------------------------
+
+WIDE_MARGINS = (51, 64, 100, 300, 1500, 3000, 10000)
+_IUPAC_SETS = {"R": "AG", "Y": "CT", "M": "AC", "K": "GT", "S": "CG", "W": "AT", "N": "ACGT"}
+
+
+def wide_lengths(W):
+    return [W, W + 1, 31, 32, 33, 40, 63, 64, 65, 97, 130]
+
+
+def wide_case(rng, tag, W, M, N, X, I, lengths, n_sts, n_rec, max_rec, tandem=False, gap=(20, 200),
+              roomy=1, tandem_width=None, min_rec=0):
+    """One planted case: (params, sts_text, records, plants).
+
+    Every STS gets amplicons in both orientations ('+': p1 .. p2, '-': p2 .. revcomp(p1)) with
+    a known product length size + d.  plants lists [kind, record, k, k + size + d - 1, id,
+    direct, d, expect]: expect 1 means the output must hold exactly that line, 0 that it must
+    not (near misses with N + 1 mismatches, a mismatch in a protected 3' base, products at
+    d = +-(M + 1)), -1 that the reference decides (genome ambiguity characters, tandem runs).
+    The first `roomy` STS have sizes of l1 + l2 + M or more, so that d = -M and -(M + 1) can be
+    planted; their plants come first, and plants that no longer fit n_rec records of max_rec
+    bases are left out.  tandem: one more STS whose primer 2 is CA x 10, with (CA) runs where
+    its tries fall (every try at M <= 400, else tandem_width tries at either end)."""
+    def acgt(n):
+        return "".join(rng.choices("ACGT", k=n)) if n > 0 else ""
+
+    def other(c, primer_c):
+        return rng.choice([b for b in "ACGT" if b != c and b != primer_c])
+
+    sts = []
+    for s in range(n_sts):
+        l1, l2 = rng.choice(lengths), rng.choice(lengths)
+        p1, p2 = list(acgt(l1)), list(acgt(l2))
+        for p in (p1, p2):                       # IUPAC letters past base 32
+            if len(p) > 34 and rng.random() < (0.5 if I else 0.15):
+                for _ in range(rng.randint(1, 2)):
+                    p[rng.randrange(32, len(p))] = rng.choice("RYMKSWN")
+        if rng.random() < 0.15 and l1 > W + 3:   # seed taken past a leading 'N' (hash_offset > 0)
+            p1[:rng.randint(1, 3)] = "N" * 3
+            p1 = p1[:l1]
+        p1, p2 = "".join(p1), "".join(p2)
+        r = rng.random()
+        if s < roomy:
+            room = M + rng.randint(0, 40)        # roomy: d = -M and -(M + 1) are plantable
+        elif r < 0.3:
+            room = rng.choice([0, 1, 5])         # lo clipped, primers overlap for d < -room
+        else:
+            room = rng.randint(20, 120)
+        size = l1 + l2 + room
+        field = str(size) if rng.random() < 0.85 or room else str(size - 3)
+        sts.append(dict(id=f"{tag}s{s}", p1=p1, p2=p2, size=size, field=field, alias=f"w {s}"))
+    if tandem:
+        l1 = rng.choice(lengths)
+        sts.append(dict(id=f"{tag}tan", p1=acgt(l1), p2="CA" * 10, size=l1 + 20 + M + rng.randint(10, 60),
+                        field=None, alias="tandem"))
+        sts[-1]["field"] = str(sts[-1]["size"])
+
+    def concrete(p):
+        out = []
+        for c in p:
+            if c in "ACGT" or not I or rng.random() < 0.3:
+                out.append(c)                    # I = 0: the letter itself is what matches
+            else:
+                out.append(rng.choice(_IUPAC_SETS[c]))
+        return out
+
+    def seed_off(p):
+        for off in range(len(p) - W + 1):
+            if all(c in "ACGT" for c in p[off:off + W]):
+                return off
+        return -1
+
+    def mutate(text, primer, positions):
+        for i in positions:
+            text[i] = other(text[i], primer[i])
+
+    def pick(allowed, n, split):
+        """n positions from allowed, preferring bases >= 32; split: both sides of base 32."""
+        late = [i for i in allowed if i >= 32]
+        early = [i for i in allowed if i < 32]
+        if split and n >= 2 and late and early:
+            got = [rng.choice(late), rng.choice(early)]
+            rest = [i for i in allowed if i not in got]
+            return got + rng.sample(rest, min(n - 2, len(rest)))
+        pool = late if late and rng.random() < 0.8 else allowed
+        if len(pool) < n:
+            pool = allowed
+        return rng.sample(pool, n) if len(pool) >= n else None
+
+    plants = []  # (kind, id, direct, d, expect, text, at_end)
+    for st in sts:
+        if st["id"].endswith("tan"):
+            continue
+        kinds = ["match", "plusM", "minusLo", "near1", "near2", "over+", "deco", "match"]
+        if N:
+            kinds += ["mm", "mm", "mm"]
+        if X:
+            kinds += ["prot1", "prot2"]
+        if st in sts[:roomy]:
+            kinds += ["over-"]
+            chosen = ["plusM", "minusLo", "over-", "over+"] + rng.sample(kinds, 2)
+        else:
+            chosen = rng.sample(kinds, min(len(kinds), rng.randint(3, 5)))
+        if M >= 1500 and st not in sts[:roomy]:
+            chosen = [k for k in chosen if k not in ("plusM", "over+")] or ["match"]
+        for kind in chosen:
+            direct = rng.choice("+-")
+            a, b = (st["p1"], st["p2"]) if direct == "+" else (st["p2"], _rc(st["p1"]))
+            la, lb = len(a), len(b)
+            off = seed_off(a)
+            if off < 0:
+                continue
+            e = st["size"]
+            lo = max(0, min(M, e - la - lb))
+            ta, tb = concrete(a), concrete(b)
+            ok_a = [i for i in range(la) if a[i] in "ACGT" and not off <= i < off + W and i < la - X]
+            ok_b = [i for i in range(lb) if b[i] in "ACGT" and i >= X]
+            expect = 1
+            d = rng.choice([0, rng.randint(-lo, M), rng.randint(-lo, min(M, 60))])
+            if kind == "plusM":
+                d = M
+            elif kind == "minusLo":
+                d = -lo
+            elif kind == "over+":
+                d, expect = M + 1, 0
+            elif kind == "over-":
+                if e - la - lb < M + 1:
+                    continue
+                d, expect = -(M + 1), 0
+            elif kind == "mm":
+                for t, p, ok in ((ta, a, ok_a), (tb, b, ok_b)):
+                    if ok and rng.random() < 0.75:
+                        pos = pick(ok, min(len(ok), rng.randint(1, N)), False)
+                        mutate(t, p, pos)
+            elif kind in ("near1", "near2"):
+                t, p, ok = (ta, a, ok_a) if kind == "near1" else (tb, b, ok_b)
+                pos = pick(ok, N + 1, True)
+                if pos is None:
+                    continue
+                mutate(t, p, pos)
+                expect = 0
+            elif kind in ("prot1", "prot2"):
+                if kind == "prot1":
+                    ok = [i for i in range(max(0, la - X), la) if a[i] in "ACGT" and not off <= i < off + W]
+                else:
+                    ok = [i for i in range(min(X, lb)) if b[i] in "ACGT"]
+                if not ok:
+                    continue
+                late = [i for i in ok if i >= 32]
+                i = rng.choice(late or ok)
+                mutate(ta if kind == "prot1" else tb, a if kind == "prot1" else b, [i])
+                expect = 0
+            elif kind == "deco":                 # genome ambiguity characters under the primers
+                for t, ok in ((ta, ok_a), (tb, ok_b)):
+                    if ok:
+                        t[rng.choice(ok)] = rng.choice("NRU")
+                expect = -1
+            fill = list(acgt(e + d - la - lb))
+            if fill and rng.random() < 0.3:      # ... and inside the tries' stretch
+                fill[rng.randrange(len(fill))] = rng.choice("NRU")
+            at_end = expect == 1 and kind == "match" and rng.random() < 0.5
+            if at_end:                           # ends the record: hi = 0, or e truncated for d < 0
+                d = rng.choice([0, -min(lo, 3), -min(lo, 7)])
+                fill = list(acgt(e + d - la - lb))
+            plants.append((kind, st["id"], direct, d, expect, "".join(ta) + "".join(fill) + "".join(tb), at_end, e))
+    rng.shuffle(plants)
+    first = {st["id"] for st in sts[:roomy]}
+    plants.sort(key=lambda pl: pl[1] not in first)
+    if tandem:
+        st = sts[-1]
+        a, e = st["p1"], st["size"]
+        tw = tandem_width or (160 if M > 3000 else 300 if M > 1500 else 500)
+        spans = [(-M, M)] if M <= 400 else [(-M, -M + tw), (M - tw, M)]
+        text = a
+        for d0, d1 in spans:
+            start = e - 20 + d0                   # primer 2's window at try d0
+            text += acgt(start - len(text)) + "CA" * ((d1 - d0 + 20) // 2)
+        plants.insert(0, ("tandem", st["id"], "+", 0, -1, text, True, 0))
+
+    records, meta = [], []
+    cur, has_end, need = [], False, 0
+    plain = [st for st in sts if not st["id"].endswith("tan")]
+
+    def close():
+        """End the record; unless a plant ends it, every plant keeps its whole size ahead of it
+        (a record that ends sooner truncates the size and shifts the tries)."""
+        nonlocal cur, has_end, need
+        if cur:
+            if not has_end:
+                cur.append(acgt(max(rng.randint(*gap), need - sum(map(len, cur)))))
+                st = rng.choice(plain)           # an exact product on the record's last bases: hi = 0
+                direct = rng.choice("+-")
+                a, b = (st["p1"], st["p2"]) if direct == "+" else (st["p2"], _rc(st["p1"]))
+                if seed_off(a) >= 0:
+                    text = "".join(concrete(a)) + acgt(st["size"] - len(a) - len(b)) + "".join(concrete(b))
+                    k = sum(map(len, cur))
+                    cur.append(text)
+                    meta.append(["end", len(records), k, k + len(text) - 1, st["id"], direct, 0, 1])
+            records.append("".join(cur))
+        cur, has_end, need = [], False, 0
+
+    for kind, sid, direct, d, expect, text, at_end, e in plants:
+        n = sum(map(len, cur))
+        if has_end or (cur and n + len(text) + gap[1] > max_rec):
+            close()
+        if len(records) >= n_rec:
+            break
+        cur.append(acgt(rng.randint(*gap) if cur or rng.random() < 0.8 else 0))
+        k = sum(map(len, cur))
+        cur.append(text.lower() if rng.random() < 0.1 else text)
+        # a plant ends the record unless the record is still short of min_rec bases or an
+        # earlier plant needs it longer
+        has_end = at_end and need <= k + len(text) and k + len(text) >= min_rec
+        if not has_end:
+            need = max(need, k + e)
+        meta.append([kind, len(records), k, k + len(text) - 1, sid, direct, d, expect])
+    if len(records) < n_rec:
+        close()
+    params = dict(wordsize=W, margin=M, mismatches=N, three_prime_match=X, iupac_mode=I,
+                  default_pcr_size=240)
+    sts_text = "".join(f"{s['id']}\t{s['p1']}\t{s['p2']}\t{s['field']}\t{s['alias']}\n" for s in sts)
+    recs = [(f">{tag}r{i} wide", s) for i, s in enumerate(records)]
+    return params, sts_text, recs, meta
+
+
+def wide_plan():
+    """(W, M, N, X, I, tandem) of every --wide case: each W of the hashed table against the
+    small margins, W 8/11 against every margin, one tandem case per margin."""
+    g = random.Random(41)
+    plan = []
+    for W in (14, 15, 16):
+        for j in range(12):
+            M = (51, 64, 100, 300, 51, 64, 100, 300, 1500, 3000, 64, 100)[j]
+            plan.append((W, M, j % 4, g.choice([0, 1, 2, 4, 40]), j % 2, False))
+    for M in WIDE_MARGINS:
+        for W in (8, 11):
+            for j in range(2 if M <= 300 else 1):
+                plan.append((W, M, g.randint(0, 3), g.choice([0, 1, 2, 4, 40]), g.randint(0, 1), False))
+        plan.append((g.choice([8, 11, 14, 16]), M, g.randint(0, 1), g.choice([0, 1, 2]), 0, True))
+    return plan
+
+
+def wide_cases(seed=20261019):
+    rng = random.Random(seed)
+    cases = []
+    for i, (W, M, N, X, I, tandem) in enumerate(wide_plan()):
+        big = M >= 1500
+        n_sts = rng.randint(2, 3) if big else rng.randint(2, 15)
+        if tandem:
+            n_sts = 2
+        params, sts_text, recs, plants = wide_case(
+            rng, f"w{i}", W, M, N, X, I, wide_lengths(W), n_sts, 3 if big else rng.randint(1, 3),
+            40000 if big else rng.randint(2000, 9000), tandem=tandem)
+        case = {"params": params, "sts_text": sts_text, "records": [list(r) for r in recs], "plants": plants}
+        case.update(run_ref(params, sts_text, records=recs))
+        cases.append(case)
+    return cases
+
+
+def wide_tally(cases):
+    """What the wide corpus holds, counted with this repository's oracle from the recorded
+    inputs and outputs (tests/test_oracle_golden.py asserts the floors)."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import c_oracle as C
+    from oracle import epcr_oracle as O
+    t = dict(cases=len(cases), hits=0, l1_33=0, l2_33=0, l1_65=0, l2_65=0, mm_ge32=0, mm_ge64=0, d_plus_m=0,
+             d_minus_m=0, near_absent=0, over_absent=0, prot_absent=0, planted_found=0, last_base=0,
+             truncated=0, hash_offset=0, tandem_max=0, by_w={}, by_m={})
+    for case in cases:
+        prm = case["params"]
+        p = O.params(**prm)
+        table = O.load_sts_lines(case["sts_text"].splitlines(True), prm["wordsize"], prm["default_pcr_size"])
+        out = set(case["output"].splitlines())
+        t["by_w"][prm["wordsize"]] = t["by_w"].get(prm["wordsize"], 0) + 1
+        t["by_m"][prm["margin"]] = t["by_m"].get(prm["margin"], 0) + 1
+        labels = [O.fasta_label(d) for d, _ in case["records"]]
+        for kind, r, k, end, sid, direct, d, expect in case["plants"]:
+            alias = next(x.alias for x in table.records if x.sts_id == sid)
+            line = f"{labels[r]}\t{k + 1}..{end + 1}\t{sid}\t{alias}\t({direct})"
+            if expect == 1:
+                assert line in out, (prm, kind, line)
+                t["planted_found"] += 1
+                t["d_plus_m"] += d == prm["margin"]
+                t["d_minus_m"] += d == -prm["margin"]
+            elif expect == 0:
+                assert line not in out, (prm, kind, line)
+                t["near_absent"] += kind.startswith("near")
+                t["over_absent"] += kind.startswith("over")
+                t["prot_absent"] += kind.startswith("prot")
+        found = C.search(table, [s.encode() for _, s in case["records"]], p, 1)
+        assert len(found) == case["n_hits"], prm
+        for q, (_, seq) in enumerate(case["records"]):
+            S = seq.upper()
+            per = {}
+            mine = found[found["seq"] == q]
+            for k, pos2, ri in zip(mine["pos1"].tolist(), mine["pos2"].tolist(), mine["rec"].tolist()):
+                rec = table.records[ri]
+                l1, l2 = len(rec.primer1), len(rec.primer2)
+                t["hits"] += 1
+                t["l1_33"] += l1 > 32
+                t["l2_33"] += l2 > 32
+                t["l1_65"] += l1 > 64
+                t["l2_65"] += l2 > 64
+                t["last_base"] += pos2 == len(S) - 1
+                t["truncated"] += rec.pcr_size > len(S) - k
+                t["hash_offset"] += rec.hash_offset > 0
+                per[(k, ri)] = per.get((k, ri), 0) + 1
+                late = 0
+                for w, pr, strand in ((S[k:k + l1], rec.primer1, "+"), (S[pos2 + 1 - l2:pos2 + 1], rec.primer2, "-")):
+                    bad = [i for i in range(32, len(pr))
+                           if not O.primer_match(w[i], pr[i], strand, 0, 0, prm["iupac_mode"])]
+                    late = max([late] + bad)
+                t["mm_ge32"] += late >= 32
+                t["mm_ge64"] += late >= 64
+            t["tandem_max"] = max([t["tandem_max"]] + list(per.values()))
+    return t
+
+
 def main():
+    if "--wide" in sys.argv:
+        logging.disable(logging.CRITICAL)
+        cases = wide_cases()
+        print("wide:", json.dumps(wide_tally(cases)), file=sys.stderr)
+        with gzip.open(os.path.join(HERE, "wide.json.gz"), "wt") as fh:
+            json.dump({"cases": cases}, fh, separators=(",", ":"))
+        return
     if "--errors" in sys.argv:
         erng = random.Random(2026)
         obj = error_cases(erng)

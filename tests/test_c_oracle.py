@@ -17,7 +17,7 @@ def _lines(case, nthreads=1):
 
 @pytest.mark.parametrize("nthreads", [1, 3])
 def test_c_oracle_golden(nthreads):
-    for name in ("random_cases.json.gz", "special_cases.json.gz"):
+    for name in ("random_cases.json.gz", "special_cases.json.gz", "wide.json.gz"):
         for i, case in enumerate(load_golden(name)["cases"]):
             got = _lines(case, nthreads)
             if not case["load_ok"]:

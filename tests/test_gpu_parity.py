@@ -104,7 +104,7 @@ def test_dense_repeat_order(bits):
 
 
 @pytest.mark.parametrize("tails", ["auto", "inline", "kernel"])
-@pytest.mark.parametrize("name", ["random_cases.json.gz", "special_cases.json.gz"])
+@pytest.mark.parametrize("name", ["random_cases.json.gz", "special_cases.json.gz", "wide.json.gz"])
 def test_golden_corpus(name, tails):
     """Every recorded reference case through the default kernels (dense_kernel for W <= 9),
     and again through scan_kernel with the multi-record bucket tails forced to each of its
@@ -170,6 +170,21 @@ def test_device_sort_crowded_buckets(bits):
                 recs = _records(case, eng, td)
             if _device_lines(eng, recs) != case["output"].splitlines():
                 bad.append((name, i))
+    assert not bad, bad[:5]
+
+
+def test_device_sort_crowded_buckets_wide():
+    """The wide corpus (hashed tables, margins to 10,000: try ranks to 20,000 in the sort key,
+    hundreds of hits of one survivor) through 2 forced device-sort buckets."""
+    bad = []
+    for i, case in enumerate(load_golden("wide.json.gz")["cases"]):
+        eng = _engine(case["params"])
+        eng.search_options = dict(sort_bucket_bits=1)
+        with tempfile.TemporaryDirectory() as td:
+            assert _load_sts(eng, case["sts_text"], td)
+            recs = _records(case, eng, td)
+        if _device_lines(eng, recs) != case["output"].splitlines():
+            bad.append((i, case["params"]))
     assert not bad, bad[:5]
 
 
@@ -379,10 +394,11 @@ def test_dense_filter_edge_cases(W, I, N, X):
     assert len(hits) == len(ref) and hits.tobytes() == ref.tobytes()
 
 
-@pytest.mark.parametrize("W", [11, 12])
+@pytest.mark.parametrize("W", [11, 12, 14, 16])
 def test_seed_queue_rounds(W):
-    """Every window a seed (a periodic genome whose 11/12-mers are all keys): the scan
-    kernel's per-wave seed queue overflows and drains in rounds; against the C oracle."""
+    """Every window a seed (a periodic genome whose W-mers are all keys; W = 14 and 16 through
+    the hashed table): the scan kernel's per-wave seed queue overflows and drains in rounds;
+    against the C oracle."""
     from oracle import c_oracle as C
     rng = np.random.default_rng(W)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -559,12 +575,13 @@ def _multi_case(W, n_sts, seed):
 @pytest.mark.parametrize("W,n_sts,opts", [(8, 3000, {}), (10, 3000, {}), (11, 6000, {}),
                                           (11, 6000, dict(tails="inline")), (11, 6000, dict(defer=False)),
                                           (12, 6000, {}), (11, 6000, dict(scan_grid=37)),
-                                          (11, 6000, dict(ref32=True)), (8, 3000, dict(ref32=True))])
+                                          (11, 6000, dict(ref32=True)), (8, 3000, dict(ref32=True)),
+                                          (14, 6000, {}), (16, 6000, {}), (16, 6000, dict(tails="inline"))])
 def test_sharded_ranges_all_paths(W, n_sts, opts):
     """Owned (seq, k) ranges partition the hit list exactly through every scan path:
     dense_kernel or the split seeds (W=8), the exact-LDS scan (W=10), the key-group scan with
     its references to tail_kernel (W=11 default; 16-B and, with ref32, 32-B references),
-    inline tails, no deferral; cuts inside super-steps and next to records' seed offsets
+    the hashed table (W = 14, 16), inline tails, no deferral; cuts inside super-steps and next to records' seed offsets
     (k + hash_offset straddling a cut)."""
     from merpcr_amd import _native
     sts_text, seqs = _multi_case(W, n_sts, 30 + W)

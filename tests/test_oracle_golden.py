@@ -88,7 +88,7 @@ def test_dense_repeat():
     assert lines == _expected_lines(case)
 
 
-@pytest.mark.parametrize("name", ["random_cases.json.gz", "special_cases.json.gz"])
+@pytest.mark.parametrize("name", ["random_cases.json.gz", "special_cases.json.gz", "wide.json.gz"])
 def test_random_corpus(name):
     cases = load_golden(name)["cases"]
     for i, case in enumerate(cases):
@@ -102,6 +102,30 @@ def test_random_corpus(name):
         if "fasta" in case:
             fr = O.fasta_from_lines(io.StringIO(case["fasta_text"], newline=None))
             assert [[d, s] for d, s in fr] == [[d, s] for d, s, _ in case["fasta"]], i
+
+
+def test_wide_corpus_tally():
+    """What wide.json.gz (make_golden.py --wide) must hold to be worth having, re-counted from the
+    recorded inputs and outputs with the oracle: hashed-table word sizes, primers past one and
+    two 32-base chunks on either side, mismatches that only a later chunk sees, products at
+    d = +-M, planted near misses (N + 1 mismatches, a protected 3' base) and d = +-(M + 1)
+    products that the reference did not report, every margin, a tandem survivor with hundreds
+    of tries that hit.  wide_tally itself asserts every planted line present or absent."""
+    from tests.golden.make_golden import WIDE_MARGINS, wide_tally
+    cases = load_golden("wide.json.gz")["cases"]
+    t = wide_tally(cases)
+    print(t)
+    assert 60 <= t["cases"] <= 100
+    assert all(t["by_w"].get(W, 0) >= 8 for W in (14, 15, 16)), t["by_w"]
+    assert t["by_w"].get(8, 0) > 0 and t["by_w"].get(11, 0) > 0
+    assert all(t["by_m"].get(M, 0) >= 1 for M in WIDE_MARGINS), t["by_m"]
+    assert t["hits"] >= 300 and t["hits"] == sum(c["n_hits"] for c in cases)
+    for k in ("l1_33", "l2_33", "l1_65", "l2_65", "mm_ge32"):
+        assert t[k] >= 20, (k, t)
+    assert t["d_plus_m"] >= 10 and t["d_minus_m"] >= 10, t
+    assert t["near_absent"] + t["prot_absent"] >= 20 and t["near_absent"] >= 20 and t["over_absent"] >= 10, t
+    assert t["prot_absent"] > 0 and t["last_base"] > 0 and t["truncated"] > 0 and t["hash_offset"] > 0, t
+    assert t["tandem_max"] > 200, t
 
 
 def test_threaded_chunk_semantics():
